@@ -10,7 +10,18 @@ out of place so every step sees the same input. Multi-GPU runs are replicas
 path; torch.distributed over gloo is used only for the barrier, the
 max-over-ranks clock and the per-rank report), so scaling is weak.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: control plane,
+stream, placement, settle, W warm-up and K timed steps, the result line.
+--full adds every other leg to the same line: the same stream on unplaced and
+on plain allocations, packed 32-byte prefixes, the PCIe-inclusive host path
+and the CPU baseline (each with its own --no-... switch).
+
+--dump-outputs DIR writes what the K-th timed step left in the output buffers
+(header lines and verdicts of a fixed, seeded sample of the batch) as
+DIR/<name>.npy; the stream is seeded, so two builds can be compared value
+for value.
 
 --gpus N > 1 without a launcher: this process starts N fresh rank processes
 itself (grout_amd.replicas.spawn) before any GPU call and exits with their
@@ -92,6 +103,10 @@ def cpu_placement(n, policy="spread"):
 def b_pkt(fib_entry_bytes, out_bytes=64):
     return 64 + 8 + fib_entry_bytes + out_bytes + 8
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md, HBM3E spec peak
+# --dump-outputs: packets of the batch sampled (float32 lines + float64
+# verdicts and indices: 2^17 * (64 * 4 + 4 * 8 + 8) B = 37 MiB), and their seed
+DUMP_SAMPLE = 1 << 17
+DUMP_SEED = 0x64756D70
 
 
 def parse():
@@ -99,6 +114,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also measure the legs beside the headline figure: unplaced and plain allocations, packed "
+                        "32-byte prefixes, the host-memory path, the CPU baseline (see the --no-... switches)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's header lines and verdicts (a fixed, seeded "
+                        f"sample of {DUMP_SAMPLE} packets of the batch) as DIR/<name>.npy")
     p.add_argument("--batch", type=int, default=None,
                    help="packets per step per GPU (default 2^24; 2^22 for imix_frames, 8 GiB of 2 KiB slots)")
     p.add_argument("--workload", default="fullview64",
@@ -113,7 +134,7 @@ def parse():
                         "--candidates allocations; plain: torch allocations")
     p.add_argument("--candidates", type=int, default=8)
     p.add_argument("--no-plain", action="store_true",
-                   help="skip the same measurement on plain torch allocations (value_plain_placement)")
+                   help="--full: skip the same measurement on plain torch allocations (value_plain_placement)")
     p.add_argument("--time-every", type=int, default=4,
                    help="HIP events around every N-th launch only (the kernel time is their average; "
                         "each event pair costs ~7 us of stream time)")
@@ -121,16 +142,24 @@ def parse():
                    help="line: each packet's whole 64-byte header line written back (BASELINE.md's 148 B); prefix32: "
                         "packed 32-byte prefixes, every byte the path changes (GR_HIP_BATCH_F_PREFIX32)")
     p.add_argument("--no-prefix-leg", action="store_true",
-                   help="skip the same measurement with packed 32-byte output prefixes (prefix32 in the line)")
+                   help="--full: skip the same measurement with packed 32-byte output prefixes (prefix32 in the line)")
     p.add_argument("--settle-ms", type=float, default=100.0,
                    help="before the --warmup steps of each leg, run the same step untimed for this long: after the "
                         "idle gap of the stream upload the GPU takes ~20-40 launches to reach its steady clock "
                         "(tools/clock_probe.py); the forwarding plane's throughput is its steady-state rate")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-host-path", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    p.add_argument("--no-host-path", action="store_true", help="--full: skip the host-memory path")
     p.add_argument("--cpu-seconds", type=float, default=6.0, help="wall time of the CPU baseline sample")
     p.add_argument("--cpu-threads", type=int, default=16, help="host cores of the box share (16)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps >= 1 and --warmup >= 0")
+    # the legs beside the headline figure run under --full only
+    args.no_plain |= not args.full
+    args.no_prefix_leg |= not args.full
+    args.no_host_path |= not args.full
+    args.no_cpu_baseline |= not args.full
+    return args
 
 
 def log(*a):
@@ -303,6 +332,36 @@ def main():
 
     tmax, kern_ms, kcount = measure((d_in, d_out, d_meta, d_v), args.steps, args.warmup)
     own_s = measure.own
+
+    # ---- --dump-outputs: what the last timed step wrote, for a sample of the
+    # batch drawn with a fixed seed (the same packets in every run of the same
+    # arguments), read back in chunks of 2^20 packets
+    if args.dump_outputs:
+        k = min(n, DUMP_SAMPLE)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False)) if k < n else np.arange(n)
+        s_lines = np.empty((k, out_bytes), dtype=np.uint8)
+        s_v = np.empty(k, dtype=abi.VERDICT_DT)
+        chunk = 1 << 20
+        c_lines = np.empty((chunk, out_bytes), dtype=np.uint8)
+        c_v = np.empty(chunk, dtype=abi.VERDICT_DT)
+        for c0 in range(0, n, chunk):
+            cn = min(chunk, n - c0)
+            lo, hi = np.searchsorted(idx, [c0, c0 + cn])
+            if lo == hi:
+                continue
+            abi.check("gr_hip_memcpy_d2h", fp.lib.gr_hip_memcpy_d2h(
+                fp.h, c_lines.ctypes.data, abi.ptr(d_out) + c0 * out_bytes, cn * out_bytes))
+            abi.check("gr_hip_memcpy_d2h", fp.lib.gr_hip_memcpy_d2h(fp.h, c_v.ctypes.data, abi.ptr(d_v) + c0 * 8, cn * 8))
+            s_lines[lo:hi] = c_lines[idx[lo:hi] - c0]
+            s_v[lo:hi] = c_v[idx[lo:hi] - c0]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        for name, a in (("out_lines", s_lines.astype(np.float32)),  # one byte per element
+                        ("verdicts", np.stack([s_v[f].astype(np.float64) for f in abi.VERDICT_DT.names], axis=1)),
+                        ("sample_index", idx.astype(np.float64))):
+            np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), a)
+        del c_lines, c_v, s_lines, s_v
+        log(f"[rank {rank}] outputs of {k} sampled packets written to {args.dump_outputs}")
 
     if batch is not None:
         vh = np.empty(n, dtype=abi.VERDICT_DT)

@@ -34,6 +34,23 @@ def test_cpu_placement_spread():
     assert bench.cpu_placement(len(allowed) * 2 + 1) is None
 
 
+def test_plain_run_has_no_side_legs(monkeypatch):
+    """A plain run measures the headline figure alone; --full turns on every
+    other leg, each still switched off by its own --no-... option."""
+    legs = ("no_plain", "no_prefix_leg", "no_host_path", "no_cpu_baseline")
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert all(getattr(a, leg) for leg in legs)
+    a = parse("--full")
+    assert a.full and not any(getattr(a, leg) for leg in legs)
+    a = parse("--full", "--no-host-path", "--dump-outputs", "d")
+    assert a.no_host_path and not a.no_cpu_baseline and a.dump_outputs == "d"
+
+
 def test_cpu_placement_one_socket():
     p = bench.cpu_placement(1, "socket")
     if p is None:

@@ -195,15 +195,15 @@ def test_bench_two_ranks_on_the_gpu():
 def test_bench_spawns_two_ranks_on_the_gpu():
     """The driver's N>1 command without a launcher: bench.py --gpus 2 starts
     both ranks itself on config 3 (full view); one line, n_gpus 2, both
-    ranks' own rates and kernel times, and -- after the final barrier, rank
-    0 alone -- the PCIe-inclusive host path and the CPU baseline (a short
-    sample here), as on the driver's N>1 lines."""
+    ranks' own rates and kernel times, and -- with --full, after the final
+    barrier, rank 0 alone -- the PCIe-inclusive host path and the CPU baseline
+    (a short sample here), as on the driver's N>1 lines."""
     import json
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["GR_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--workload", "fullview64", "--batch", str(1 << 22),
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--full", "--workload", "fullview64", "--batch", str(1 << 22),
            "--steps", "8", "--warmup", "2", "--settle-ms", "20", "--no-prefix-leg", "--cpu-seconds", "0.3",
            "--cpu-threads", "4"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)

@@ -24,7 +24,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 stop_if_fatal $? smoke
 cat $OUT/smoke.log
 
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
 stop_if_fatal $? bench
 cat $OUT/bench.json; tail -5 $OUT/bench.err
 
