@@ -105,6 +105,9 @@ BATCH_F_FRAME_PTRS = 0x2
 BATCH_F_PREFIX32 = 0x4  # out_lines: packed 32-byte prefixes (every byte the path changes)
 PREFIX = 32
 NODE_DEPTH = 4  # GR_HIP_NODE_DEPTH: node walks in flight per queue
+# static NAT44 in the kernel (gr_hip_nat44_set) and its flags in gr_hip_verdict.domain
+NAT44_DNAT_STATIC, NAT44_SNAT_STATIC = 0x1, 0x2
+VERDICT_DNAT, VERDICT_SNAT, VERDICT_DOMAIN_MASK = 0x80, 0x40, 0x3F
 
 
 class Batch(ctypes.Structure):
@@ -151,6 +154,11 @@ HIP_API = {
     "gr_hip_iface_del": (_I, [_P, _U16]),
     "gr_hip_nh_set": (_I, [_P, _U32, _P, _U32]),
     "gr_hip_reta_set": (_I, [_P, _U32, _P, _U32]),
+    "gr_hip_nat44_set": (_I, [_P, _U32]),
+    "gr_hip_nat44_get": (_I, [_P]),
+    "gr_hip_snat44_static_add": (_I, [_P, _U16, _U32, _U32]),
+    "gr_hip_snat44_static_del": (_I, [_P, _U16, _U32]),
+    "gr_hip_snat44_static_clear": (_I, [_P]),
     "gr_hip_fib4_create": (_I, [_P, _U16, _U32, _U32]),
     "gr_hip_fib4_destroy": (_I, [_P, _U16]),
     "gr_hip_route4_add": (_I, [_P, _P, _U32, _I]),

@@ -240,25 +240,88 @@ __device__ __forceinline__ uint32_t chain_fib(const rxv &rx, uint32_t dst) {
 	return ent;
 }
 
-// From the adjacency (its first 32 bytes in a, b) to the verdict:
-// group resolution, ip_input's nexthop checks, ip_forward, ip_output,
-// eth_output, iface_output. Rewrites row `row` of R.
-__device__ __forceinline__ void chain_tail(const kctx &P, uint8_t *R, uint32_t row, const gr_hip_pkt_meta &m,
-					  uint32_t rx_flags, result &r, uint32_t dst, uint32_t data_len, uint32_t slot,
-					  uint4 a, uint4 b) {
-	adjv A = unpack_adj(a, b, uint4{0, 0, 0, 0});
-	if (A.type == GR_HIP_NH_T_GROUP) { // nexthop_group_get_nh, nexthop.h:89-96
-		const uint4 c = gld4(reinterpret_cast<const uint4 *>(tload(&P.T->adj) + slot) + 2);
-		const uint32_t n_members = c.x & 0xffff, reta_size = c.x >> 16;
-		if (n_members == 1) {
-			slot = c.z;
-		} else if (n_members == 0) {
-			slot = 0;
-		} else {
-			uint32_t i = c.y + (m.rss & (reta_size - 1));
-			slot = i < tload(&P.T->reta_cap) ? gld(tload(&P.T->reta) + i) : 0;
+// The member of group `slot` for the packet (nexthop_group_get_nh,
+// nexthop.h:89-96), 0 = none.
+__device__ __forceinline__ uint32_t group_member(const kctx &P, const gr_hip_pkt_meta &m, uint32_t slot) {
+	const uint4 c = gld4(reinterpret_cast<const uint4 *>(tload(&P.T->adj) + slot) + 2);
+	const uint32_t n_members = c.x & 0xffff, reta_size = c.x >> 16;
+	if (n_members == 1) {
+		slot = c.z;
+	} else if (n_members == 0) {
+		slot = 0;
+	} else {
+		uint32_t i = c.y + (m.rss & (reta_size - 1));
+		slot = i < tload(&P.T->reta_cap) ? gld(tload(&P.T->reta) + i) : 0;
+	}
+	return slot <= P.max_nh ? slot : 0;
+}
+
+// fixup_checksum_32 (modules/policy/datapath/nat_datapath.h:33-46): the
+// checksum field ck after the 32-bit datum `from` became `to`, all as stored.
+__device__ __forceinline__ uint32_t nat44_fixup32(uint32_t ck, uint32_t from, uint32_t to) {
+	uint32_t sum = ~ck & 0xffff;
+	sum += (~from & 0xffff) + (to & 0xffff);
+	sum += (~from >> 16) + (to >> 16);
+	sum = (sum >> 16) + (sum & 0xffff);
+	sum += sum >> 16;
+	return ~sum & 0xffff;
+}
+
+// The static address translation of the packet in row `row`, the loop body of
+// dnat44_static_process (dnat44_static.c:20-89) with SRC false, that of
+// snat44_static_process (snat44_static.c:10-54) with SRC true: the IPv4 header
+// checksum, on a first fragment the TCP checksum or a non-zero UDP one (0
+// becomes 0xffff, RFC 768), then the address `from` -> `to` (as stored). No
+// check that the L4 header lies inside the packet, as in grout. Only the line
+// is staged: false, and no byte written, when the L4 checksum field reaches
+// past it (IHL > 8 for TCP, > 10 for UDP) -- the packet leaves to the CPU node.
+template <bool SRC>
+__device__ __forceinline__ bool nat44_rewrite(uint8_t *R, uint32_t row, uint32_t from, uint32_t to) {
+	const uint32_t ihl = (lds_get(R, row, 0).w >> 16) & 0xf;
+	u4v c1 = lds_get(R, row, 1); // w5 = c1.y: fragment_offset 20-21, proto 23; w6 = c1.z: cksum, src 0-1
+	const uint32_t proto = c1.y >> 24;
+	uint32_t l4 = 0; // offset of the L4 checksum field to fix, 0 = none
+	if ((c1.y & 0xff1f) == 0) { // rte_be_to_cpu_16(fragment_offset) & RTE_IPV4_HDR_OFFSET_MASK
+		if (proto == 6) // IPPROTO_TCP: rte_tcp_hdr.cksum
+			l4 = 14 + 4 * ihl + 16;
+		else if (proto == 17) // IPPROTO_UDP: rte_udp_hdr.dgram_cksum
+			l4 = 14 + 4 * ihl + 6;
+	}
+	if (l4 + 2 > GR_HIP_LINE)
+		return false;
+	c1.z = (c1.z & 0xffff0000u) | nat44_fixup32(lo16(c1.z), from, to);
+	if (l4 != 0) {
+		uint16_t *p = reinterpret_cast<uint16_t *>(R + row_off(row, l4 >> 4) + (l4 & 15));
+		uint32_t ck = *p;
+		if (proto == 6 || ck != 0) {
+			ck = nat44_fixup32(ck, from, to);
+			*p = (uint16_t)(proto == 17 && ck == 0 ? 0xffffu : ck);
 		}
-		if (slot == 0 || slot > P.max_nh) {
+	}
+	if (SRC) { // bytes 26-29
+		c1.z = lo16(c1.z) | (to << 16);
+		c1.w = (c1.w & 0xffff0000u) | (to >> 16);
+	} else { // bytes 30-33
+		c1.w = lo16(c1.w) | (to << 16);
+		u4v c2 = lds_get(R, row, 2);
+		c2.x = (c2.x & 0xffff0000u) | (to >> 16);
+		lds_put(R, row, 2, c2);
+	}
+	lds_put(R, row, 1, c1);
+	return true;
+}
+
+// From the adjacency (its first 32 bytes in a, b) to the verdict:
+// group resolution, ip_input's nexthop checks, dnat44_static (A.nat),
+// ip_forward, ip_output with snat44_static (A.nat), eth_output,
+// iface_output. Rewrites row `row` of R. nat: fwd4_params.nat.
+__device__ __forceinline__ void chain_tail(const kctx &P, uint8_t *R, uint32_t row, const gr_hip_pkt_meta &m,
+					  uint32_t rx_flags, uint32_t nat, result &r, uint32_t dst, uint32_t data_len,
+					  uint32_t slot, uint4 a, uint4 b) {
+	adjv A = unpack_adj(a, b, uint4{0, 0, 0, 0});
+	if (A.type == GR_HIP_NH_T_GROUP) {
+		slot = group_member(P, m, slot);
+		if (slot == 0) {
 			r.edge = GR_HIP_E_IP_ERROR_DEST_UNREACH;
 			return;
 		}
@@ -266,10 +329,39 @@ __device__ __forceinline__ void chain_tail(const kctx &P, uint8_t *R, uint32_t r
 	}
 	r.nh = slot;
 	if (A.e_in != CHAIN) {
-		r.edge = A.e_in;
-		return;
-	}
-	if ((A.flags & FWD4_ADJ_LOCAL) && dst == A.ipv4) {
+		// dnat44_static (dnat44_static.c:34-96) in the kernel: only where the
+		// nexthop type's edge is still that node
+		if (A.type != GR_HIP_NH_T_DNAT || A.e_in != GR_HIP_E_DNAT44_STATIC || !(nat & GR_HIP_NAT44_DNAT_STATIC)
+		    || !nat44_rewrite<false>(R, row, dst, A.ipv4)) {
+			r.edge = A.e_in;
+			return;
+		}
+		dst = A.ipv4;
+		r.domain |= GR_HIP_VERDICT_DNAT;
+		// fib4_lookup in the ingress iface's VRF (:73); r.rx_if is that iface
+		slot = chain_fib(load_rx(P, r.rx_if), dst);
+		r.nh = 0;
+		if (slot != 0 && slot <= P.max_nh) {
+			A = load_adj(P, slot);
+			if (A.type == GR_HIP_NH_T_GROUP) {
+				slot = group_member(P, m, slot);
+				if (slot != 0)
+					A = load_adj(P, slot);
+			}
+		} else {
+			slot = 0;
+		}
+		if (slot == 0) { // NO_ROUTE :75-76
+			r.edge = GR_HIP_E_IP_ERROR_DEST_UNREACH;
+			return;
+		}
+		r.nh = slot;
+		if ((A.flags & FWD4_ADJ_LOCAL) && dst == A.ipv4) { // LOCAL is ip_input_local :78-80,106
+			r.edge = GR_HIP_E_IP_INPUT_LOCAL;
+			return;
+		}
+		// FORWARD :81-85: ip_forward, whatever the nexthop's type
+	} else if ((A.flags & FWD4_ADJ_LOCAL) && dst == A.ipv4) {
 		r.edge = (rx_flags & FWD4_RX_SNAT_DYN) ? GR_HIP_E_IP_INPUT_LOCAL_CT : GR_HIP_E_IP_INPUT_LOCAL;
 		return;
 	}
@@ -296,6 +388,21 @@ __device__ __forceinline__ void chain_tail(const kctx &P, uint8_t *R, uint32_t r
 	if (data_len > A.mtu) {
 		r.edge = (c1.y & 0x40) ? GR_HIP_E_IP_ERROR_FRAG_NEEDED : GR_HIP_E_IP_FRAGMENT;
 		return;
+	}
+	if (A.flags & FWD4_ADJ_SNAT) { // snat44_static_process (ip_output.c:112, snat44_static.c:10-54)
+		const uint32_t src = hi16(c1.z) | (lo16(c1.w) << 16);
+		uint32_t to;
+		if (!(nat & GR_HIP_NAT44_SNAT_STATIC)) {
+			r.edge = GR_HIP_E_IP_OUTPUT_SNAT;
+			return;
+		}
+		if (snat44_lookup(P, A.oif, src, to)) { // a miss: NAT_VERDICT_CONTINUE
+			if (!nat44_rewrite<true>(R, row, src, to)) {
+				r.edge = GR_HIP_E_IP_OUTPUT_SNAT;
+				return;
+			}
+			r.domain |= GR_HIP_VERDICT_SNAT;
+		}
 	}
 	if (A.e_mid != CHAIN) {
 		r.edge = A.e_mid;

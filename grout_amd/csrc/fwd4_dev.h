@@ -143,6 +143,30 @@ __device__ __forceinline__ uint32_t vlan_lookup(const kctx &P, uint32_t parent, 
 	return 0;
 }
 
+// Static SNAT rule of (iface, src), snat44_static_lookup_translation
+// (modules/policy/control/snat44_static.c:55-64): open addressing on
+// (iface + 1) << 32 | src. False: no rule.
+__device__ __forceinline__ bool snat44_lookup(const kctx &P, uint32_t iface, uint32_t src, uint32_t &replace) {
+	const uint64_t *keys = tload(&P.T->snat_keys);
+	if (keys == nullptr)
+		return false;
+	const uint32_t *vals = tload(&P.T->snat_vals);
+	const uint32_t mask = tload(&P.T->snat_mask);
+	const uint64_t key = ((uint64_t)(iface + 1) << 32) | src;
+	uint32_t h = snat44_hash(iface, src) & mask;
+	for (uint32_t i = 0; i <= mask; i++) {
+		const uint64_t k = gld(keys + h);
+		if (k == key) {
+			replace = gld(vals + h);
+			return true;
+		}
+		if (k == 0)
+			return false;
+		h = (h + 1) & mask;
+	}
+	return false;
+}
+
 // Add to the counters of (kind, iface) in this workgroup's global shard.
 __device__ __forceinline__ void shard_add(gr_hip_iface_stats *stats, uint32_t max_ifaces, uint32_t kind, uint32_t iface,
 					  unsigned long long pkts, unsigned long long bytes) {

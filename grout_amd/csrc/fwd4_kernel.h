@@ -63,12 +63,15 @@ struct fwd4_rx6 {
 // edge-registration changes.
 #define FWD4_ADJ_LOCAL 0x01 // L3 nexthop flagged LOCAL (ip_input.c:166-168)
 #define FWD4_ADJ_LINK 0x02 // flagged LINK (ip_output.c:126-127)
+#define FWD4_ADJ_SNAT 0x04 // oif has SNAT_STATIC and not SNAT_DYNAMIC (ip_output.c:112): the kernel
+                           // runs snat44_static itself (gr_hip_nat44_set), else IP_OUTPUT_SNAT
 struct fwd4_adj {
 	uint8_t type; // GR_HIP_NH_T_*
 	uint8_t e_in; // ip_input nh type edge (CHAIN = ip_forward)
 	uint8_t flags; // FWD4_ADJ_*
 	uint8_t e_pre; // ip_output before the MTU check (nh type edge, ERROR) or CHAIN
-	uint8_t e_mid; // after it: SNAT, iface type edge, HOLD (state) or CHAIN
+	uint8_t e_mid; // after it: SNAT (a SNAT_DYNAMIC oif), iface type edge, HOLD (state) or CHAIN;
+	               // with FWD4_ADJ_SNAT: what follows the static SNAT step
 	uint8_t e_post; // eth_output / iface_output outcome
 	uint16_t oif; // mbuf_data(m)->iface set by ip_output
 	uint16_t mtu; // of oif
@@ -117,6 +120,20 @@ struct fwd4_nhf {
 	uint16_t mtu;
 };
 
+// Home slot (before the mask) of a static SNAT rule's key, host and device.
+static inline
+#ifdef __HIPCC__
+	__host__ __device__
+#endif
+	uint32_t
+	snat44_hash(uint32_t iface_id, uint32_t match) {
+	uint32_t k = match ^ (iface_id * 0x9e3779b1u);
+	k ^= k >> 16;
+	k *= 0x85ebca6bu;
+	k ^= k >> 13;
+	return k;
+}
+
 // Device-resident per-context tables (updated by the control plane under
 // quiesce, read by every launch through one pointer).
 struct fwd4_tables {
@@ -129,8 +146,14 @@ struct fwd4_tables {
 	const uint32_t *reta;
 	const uint32_t *vlan_keys; // (parent << 16 | vlan_id) + 1, 0 = empty
 	const uint16_t *vlan_vals;
+	// static SNAT rules (snat44_static_policy_add, modules/policy/control/snat44_static.c:15-30):
+	// open addressing from snat44_hash(iface_id, match) on
+	// (iface_id + 1) << 32 | match (network order as stored), 0 = empty
+	const uint64_t *snat_keys;
+	const uint32_t *snat_vals; // replace, network order as stored
 	uint32_t reta_cap;
 	uint32_t vlan_mask; // capacity - 1
+	uint32_t snat_mask; // capacity - 1
 	uint32_t max_ifaces;
 	uint32_t max_nh;
 	struct fwd4_edges edges;
@@ -167,7 +190,7 @@ struct fwd4_params {
 	// addresses (GR_HIP_BATCH_F_FRAME_PTRS)
 	uint32_t wg0, wgs;
 	uint32_t ptrs;
-	uint32_t _pad;
+	uint32_t nat; // GR_HIP_NAT44_* the chain runs itself for this batch (0 with GR_HIP_BATCH_F_PREFIX32)
 };
 
 // The resident kernel's batches: ring r of a context holds `ndesc`

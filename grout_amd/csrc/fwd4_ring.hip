@@ -380,7 +380,7 @@ __device__ void ring_compute(const fwd4_params &A, const kctx &P, LT &L, stat_sl
 					fast_tail(R, lane, r, data_len, slot, f);
 				} else {
 					const uint4 *ap = reinterpret_cast<const uint4 *>(tload(&P.T->adj) + slot);
-					chain_tail(P, R, lane, m, rx.flags, r, dst, data_len, slot, gld4(ap), gld4(ap + 1));
+					chain_tail(P, R, lane, m, rx.flags, A.nat, r, dst, data_len, slot, gld4(ap), gld4(ap + 1));
 				}
 			}
 		};

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <atomic>
 #include <errno.h>
+#include <map>
 #include <mutex>
 #include <shared_mutex>
 #include <new>
@@ -363,6 +364,14 @@ struct gr_hip_ctx {
 	uint32_t vlan_cap;
 	std::vector<uint32_t> vlan_keys_h; // host image of the VLAN table (node hand-back counters)
 	std::vector<uint16_t> vlan_vals_h;
+	// static NAT44 (gr_hip_nat44_set, gr_hip_snat44_static_*): the steps the
+	// kernel runs itself, the static SNAT rules by (iface_id + 1) << 32 | match,
+	// and their device table (fwd4_tables.snat_keys)
+	std::atomic<uint32_t> nat_mask{0};
+	std::map<uint64_t, uint32_t> snat_rules;
+	uint64_t *d_snat_keys = nullptr;
+	uint32_t *d_snat_vals = nullptr;
+	uint32_t snat_cap = 0;
 	fwd4_edges edges;
 	fwd4_tables *d_tables[2]; // device copy of what every launch reads, by generation
 	std::vector<gr_hip_queue *> queues;
@@ -650,7 +659,12 @@ static fwd4_adj make_adj(const gr_hip_ctx *c, uint32_t slot) {
 	a.oif = oif->id;
 	a.mtu = oif->mtu;
 	e = oif->type < 8 ? E.out_iface[oif->type] : GR_HIP_EDGE_CHAIN;
-	if (oif->flags & (GR_HIP_IFACE_F_SNAT_STATIC | GR_HIP_IFACE_F_SNAT_DYNAMIC))
+	// static SNAT alone: the kernel's own step (or IP_OUTPUT_SNAT, by the
+	// launch's fwd4_params.nat), then what follows it; with SNAT_DYNAMIC the
+	// CPU node takes everything (it runs the static lookup first itself)
+	if ((oif->flags & GR_HIP_IFACE_F_SNAT_STATIC) && !(oif->flags & GR_HIP_IFACE_F_SNAT_DYNAMIC))
+		a.flags |= FWD4_ADJ_SNAT;
+	if (oif->flags & GR_HIP_IFACE_F_SNAT_DYNAMIC)
 		a.e_mid = GR_HIP_E_IP_OUTPUT_SNAT;
 	else if (e != GR_HIP_EDGE_CHAIN)
 		a.e_mid = e;
@@ -771,6 +785,9 @@ static int upload_tables(gr_hip_ctx *c) {
 		t[g].vlan_vals = c->d_vlan_vals;
 		t[g].reta_cap = c->d_reta ? (uint32_t)c->reta.size() : 0;
 		t[g].vlan_mask = c->vlan_cap ? c->vlan_cap - 1 : 0;
+		t[g].snat_keys = c->d_snat_keys;
+		t[g].snat_vals = c->d_snat_vals;
+		t[g].snat_mask = c->snat_cap ? c->snat_cap - 1 : 0;
 		t[g].max_ifaces = c->max_ifaces;
 		t[g].max_nh = c->max_nh;
 		t[g].edges = c->edges;
@@ -991,6 +1008,8 @@ extern "C" int gr_hip_fini(gr_hip_ctx_t *c) {
 	hipFree(c->d_reta);
 	hipFree(c->d_vlan_keys);
 	hipFree(c->d_vlan_vals);
+	hipFree(c->d_snat_keys);
+	hipFree(c->d_snat_vals);
 	for (int i = 0; i < 2; i++) {
 		hipHostFree(c->stage[i]);
 		if (c->stage_ev[i])
@@ -1182,6 +1201,96 @@ static int upload_vlans(gr_hip_ctx *c) {
 		r = upload_tables(c);
 	}
 	return r;
+}
+
+// Rebuild the device table of the static SNAT rules (fwd4_tables.snat_keys):
+// a power-of-two capacity kept at load factor <= 1/2, linear probing from
+// snat44_hash. Caller holds c->mu exclusively and has quiesced.
+static int upload_snat(gr_hip_ctx *c) {
+	const size_t n = c->snat_rules.size();
+	uint32_t cap = c->snat_cap ? c->snat_cap : 16; // grown, never shrunk
+	while (cap < 2 * n)
+		cap *= 2;
+	std::vector<uint64_t> keys(cap, 0);
+	std::vector<uint32_t> vals(cap, 0);
+	for (const auto &kv : c->snat_rules) {
+		uint32_t h = snat44_hash((uint32_t)(kv.first >> 32) - 1, (uint32_t)kv.first) & (cap - 1);
+		while (keys[h] != 0)
+			h = (h + 1) & (cap - 1);
+		keys[h] = kv.first;
+		vals[h] = kv.second;
+	}
+	if (cap != c->snat_cap) {
+		hipFree(c->d_snat_keys);
+		hipFree(c->d_snat_vals);
+		c->d_snat_keys = nullptr;
+		c->d_snat_vals = nullptr;
+		c->snat_cap = 0;
+		HCK(hipMalloc(&c->d_snat_keys, cap * sizeof(uint64_t)));
+		HCK(hipMalloc(&c->d_snat_vals, cap * sizeof(uint32_t)));
+		c->snat_cap = cap;
+	}
+	int r = h2d(c, c->d_snat_keys, keys.data(), cap * sizeof(uint64_t));
+	if (r == 0)
+		r = h2d(c, c->d_snat_vals, vals.data(), cap * sizeof(uint32_t));
+	if (r == 0)
+		r = ctl_sync(c); // the vectors go out of scope
+	if (r == 0)
+		r = upload_tables(c);
+	return r;
+}
+
+static int snat_change(gr_hip_ctx *c) {
+	hipSetDevice(c->dev);
+	int r = quiesce(c);
+	if (r == 0)
+		r = upload_snat(c);
+	return r;
+}
+
+extern "C" int gr_hip_nat44_set(gr_hip_ctx_t *c, uint32_t mask) {
+	if (c == nullptr || (mask & ~(uint32_t)(GR_HIP_NAT44_DNAT_STATIC | GR_HIP_NAT44_SNAT_STATIC)))
+		return -EINVAL;
+	// like the mirrors: a submit runs entirely with the old mask or the new one
+	std::lock_guard<std::shared_mutex> l(c->mu);
+	c->nat_mask.store(mask, std::memory_order_relaxed);
+	return 0;
+}
+
+extern "C" int gr_hip_nat44_get(gr_hip_ctx_t *c) {
+	return c == nullptr ? -EINVAL : (int)c->nat_mask.load(std::memory_order_relaxed);
+}
+
+extern "C" int gr_hip_snat44_static_add(gr_hip_ctx_t *c, uint16_t iface_id, uint32_t match_be, uint32_t replace_be) {
+	if (c == nullptr || iface_id == 0 || iface_id >= c->max_ifaces)
+		return -EINVAL;
+	std::lock_guard<std::shared_mutex> l(c->mu);
+	const uint64_t key = ((uint64_t)(iface_id + 1u) << 32) | match_be;
+	if (!c->snat_rules.emplace(key, replace_be).second)
+		return -EEXIST;
+	const int r = snat_change(c);
+	if (r) // not on the device: not a rule
+		c->snat_rules.erase(key);
+	return r;
+}
+
+extern "C" int gr_hip_snat44_static_del(gr_hip_ctx_t *c, uint16_t iface_id, uint32_t match_be) {
+	if (c == nullptr)
+		return -EINVAL;
+	std::lock_guard<std::shared_mutex> l(c->mu);
+	if (c->snat_rules.erase(((uint64_t)(iface_id + 1u) << 32) | match_be) == 0)
+		return -ENOENT;
+	return snat_change(c);
+}
+
+extern "C" int gr_hip_snat44_static_clear(gr_hip_ctx_t *c) {
+	if (c == nullptr)
+		return -EINVAL;
+	std::lock_guard<std::shared_mutex> l(c->mu);
+	if (c->snat_rules.empty())
+		return 0;
+	c->snat_rules.clear();
+	return snat_change(c);
 }
 
 extern "C" int gr_hip_iface_set(gr_hip_ctx_t *c, const struct gr_hip_iface *ifs, uint32_t n) {
@@ -2145,6 +2254,13 @@ static bool host_dev_ptr(const void *p, void **dp) {
 	return true;
 }
 
+// The static NAT steps the kernel runs for batch b (fwd4_params.nat): the
+// context's mask, none for 32-byte prefixes (the destination address and the
+// L4 checksums lie past them). Caller holds c->mu.
+static uint32_t batch_nat(const gr_hip_ctx *c, const gr_hip_batch *b) {
+	return (b->flags & GR_HIP_BATCH_F_PREFIX32) ? 0 : c->nat_mask.load(std::memory_order_relaxed);
+}
+
 static int launch(gr_hip_queue *q, hipStream_t s, const gr_hip_batch *b, bool timed) {
 	gr_hip_ctx *c = q->ctx;
 	fwd4_params A{};
@@ -2168,6 +2284,7 @@ static int launch(gr_hip_queue *q, hipStream_t s, const gr_hip_batch *b, bool ti
 	A.readable = (b->flags & GR_HIP_BATCH_F_LINES_ONLY) ? GR_HIP_LINE
 		: (b->flags & GR_HIP_BATCH_F_FRAME_PTRS)    ? UINT32_MAX // whole frames
 							    : b->in_stride;
+	A.nat = batch_nat(c, b);
 	A.nhf_lds = 0;
 	int stats = c->stats_on && q->d_stats != nullptr;
 	uint32_t slot = (uint32_t)(q->n_launch % N_TIMED);
@@ -2625,6 +2742,7 @@ static int res_post(gr_hip_queue *q, const gr_hip_batch *b, res_mark *m) {
 	A.readable = (b->flags & GR_HIP_BATCH_F_LINES_ONLY) ? GR_HIP_LINE
 		: (b->flags & GR_HIP_BATCH_F_FRAME_PTRS)    ? UINT32_MAX
 							    : b->in_stride;
+	A.nat = batch_nat(c, b);
 	A.spin_max = c->spin_max;
 	A.err = q->d_err;
 	A.wgs = k;

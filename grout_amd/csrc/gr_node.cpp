@@ -676,7 +676,7 @@ extern "C" int gr_node_apply_ex(
 				}
 			}
 			b.iface = v.iface;
-			b.domain = v.domain;
+			b.domain = v.domain & GR_HIP_VERDICT_DOMAIN_MASK; // without the kernel's NAT flags
 			b.nh = v.nh;
 		}
 		if (direct != nullptr)

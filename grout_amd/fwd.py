@@ -130,8 +130,41 @@ class FastPath:
     def tune(self, key, value=0):
         return check("gr_hip_tune", self.lib.gr_hip_tune(self.h, key.encode(), value))
 
+    # -- static NAT44 ----------------------------------------------------------
+    @staticmethod
+    def _be(ip):
+        """'a.b.c.d' or host-order int -> the address as a C uint32_t holding network byte order."""
+        if isinstance(ip, str):
+            from .topology import ip4
+            ip = ip4(ip)
+        return int.from_bytes(int(ip).to_bytes(4, "big"), "little")
+
+    def nat44_set(self, dnat=False, snat=False):
+        """Which static NAT steps the kernel runs itself (gr_hip_nat44_set); both off by default."""
+        mask = (abi.NAT44_DNAT_STATIC if dnat else 0) | (abi.NAT44_SNAT_STATIC if snat else 0)
+        check("gr_hip_nat44_set", self.lib.gr_hip_nat44_set(self.h, mask))
+
+    def nat44_get(self):
+        return check("gr_hip_nat44_get", self.lib.gr_hip_nat44_get(self.h))
+
+    def snat44_static_add(self, iface_id, match, replace):
+        check("gr_hip_snat44_static_add",
+              self.lib.gr_hip_snat44_static_add(self.h, iface_id, self._be(match), self._be(replace)))
+
+    def snat44_static_del(self, iface_id, match):
+        check("gr_hip_snat44_static_del", self.lib.gr_hip_snat44_static_del(self.h, iface_id, self._be(match)))
+
+    def snat44_static_clear(self):
+        check("gr_hip_snat44_static_clear", self.lib.gr_hip_snat44_static_clear(self.h))
+
     def load(self, topo):
-        """Push a grout_amd.topology.Topology (ifaces, nexthops, reta, FIBs)."""
+        """Push a grout_amd.topology.Topology (ifaces, nexthops, reta, FIBs, static SNAT rules)."""
+        # the rule list is the topology's (an older library under A/B,
+        # GR_HIP_AB_OLD, has no rules to clear)
+        if topo.snat44_static or hasattr(self.lib, "gr_hip_snat44_static_clear"):
+            self.snat44_static_clear()
+        for iface_id, match, replace in topo.snat44_static:
+            self.snat44_static_add(iface_id, match, replace)
         self.set_ifaces(topo.ifaces)
         if topo.n_nh:
             self.set_nexthops(topo.nh[1:topo.n_nh + 1], first=1)

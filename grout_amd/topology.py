@@ -59,6 +59,7 @@ class Topology:
         self.fibs = {}  # vrf_id -> (max_routes, num_tbl8)
         self.routes6 = []  # list of ROUTE6_DT arrays
         self.fibs6 = {}  # vrf_id -> (max_routes, num_groups)
+        self.snat44_static = []  # (iface_id, match, replace), host-order ints
 
     # -- interfaces ---------------------------------------------------------
     def _iface(self, iface_id, itype, mode, flags, mtu, vrf_id, mac, **kw):
@@ -138,6 +139,8 @@ class Topology:
                 r["mac"] = np.frombuffer(mac_bytes(mac), np.uint8)
                 if state is None:
                     state = abi.NH_S["REACHABLE"]
+        elif nh_type == "DNAT" and ipv4 is not None:  # nexthop_info_dnat.replace
+            r["ipv4"] = ip4(ipv4) if isinstance(ipv4, str) else ipv4
         r["flags"] = flags
         r["state"] = state if state is not None else abi.NH_S["NEW"]
         return slot
@@ -149,6 +152,28 @@ class Topology:
                                 flags=abi.NH_F_LOCAL | abi.NH_F_LINK,
                                 state=abi.NH_S["REACHABLE"])
         self.add_route(self.ifaces[iface_id]["vrf_id"], f"{net.ip}/{net.network.prefixlen}", slot)
+        return slot
+
+    # -- static NAT44 -----------------------------------------------------------
+    def add_snat44_static(self, iface_id, match, replace):
+        """snat44_static_policy_add (modules/policy/control/snat44_static.c:15-30):
+        packets leaving through iface_id with source `match` get source `replace`."""
+        match = ip4(match) if isinstance(match, str) else int(match)
+        replace = ip4(replace) if isinstance(replace, str) else int(replace)
+        if any(i == iface_id and m == match for i, m, _ in self.snat44_static):
+            raise ValueError("snat44 rule exists")
+        self.snat44_static.append((iface_id, match, replace))
+
+    def add_dnat44(self, iface_id, match, replace):
+        """dnat44_add / dnat44_nh_import_info (modules/policy/api/dnat44.c:50-105,
+        125-168): a DNAT nexthop match -> replace on iface_id, the /32 route on
+        match in its VRF, the reverse static SNAT rule (iface, replace) -> match,
+        and GR_IFACE_F_SNAT_STATIC on the iface. Returns the nexthop slot."""
+        match = ip4(match) if isinstance(match, str) else int(match)
+        slot = self.add_nexthop(iface_id, ipv4=replace, nh_type="DNAT")
+        self.add_route(int(self.ifaces[iface_id]["vrf_id"]), f"{ipaddress.IPv4Address(match)}/32", slot)
+        self.add_snat44_static(iface_id, int(self.nh[slot]["ipv4"]), match)
+        self.ifaces[iface_id]["flags"] |= abi.IFACE_F_SNAT_STATIC
         return slot
 
     def add_address6(self, iface_id, cidr):

@@ -236,7 +236,9 @@ struct gr_hip_nh {
 	uint8_t af; // GR_HIP_AF_* (L3)
 	uint16_t iface_id;
 	uint16_t vrf_id;
-	uint32_t ipv4; // network byte order, as ip4_addr_t
+	uint32_t ipv4; // network byte order, as ip4_addr_t (L3); GR_HIP_NH_T_DNAT:
+	               // nexthop_info_dnat.replace, the translated destination
+	               // (network order; used with GR_HIP_NAT44_DNAT_STATIC)
 	uint8_t mac[6]; // L3
 	uint16_t reta_size; // GROUP: power of two
 	uint32_t reta_off; // GROUP: first slot of its reta in the reta table
@@ -297,12 +299,18 @@ struct gr_hip_pkt_meta {
 // Output verdict, 8 bytes per packet.
 struct gr_hip_verdict {
 	uint8_t edge; // enum gr_hip_edge
-	uint8_t domain; // eth_input_mbuf_data.domain as left by eth_input
+	uint8_t domain; // eth_input_mbuf_data.domain as left by eth_input (bits 0-5),
+	                // | GR_HIP_VERDICT_DNAT / _SNAT (never with gr_hip_nat44_set 0)
 	uint16_t iface; // mbuf_data(m)->iface at that edge (ingress iface
 	                // before ip_output, egress after it, the port after
 	                // iface_output)
 	uint32_t nh; // l3_mbuf_data.nh slot (0 = NULL)
 };
+// gr_hip_verdict.domain flags (gr_hip_nat44_set): the kernel rewrote the
+// packet's destination (dnat44_static) / source (snat44_static).
+#define GR_HIP_VERDICT_DNAT 0x80
+#define GR_HIP_VERDICT_SNAT 0x40
+#define GR_HIP_VERDICT_DOMAIN_MASK 0x3f
 
 #define GR_HIP_LINE 64 // bytes of frame header staged per packet
 
@@ -395,6 +403,39 @@ int gr_hip_iface_set(gr_hip_ctx_t *, const struct gr_hip_iface *ifaces, uint32_t
 int gr_hip_iface_del(gr_hip_ctx_t *, uint16_t iface_id);
 int gr_hip_nh_set(gr_hip_ctx_t *, uint32_t first_slot, const struct gr_hip_nh *nh, uint32_t n);
 int gr_hip_reta_set(gr_hip_ctx_t *, uint32_t first, const uint32_t *slots, uint32_t n);
+
+// Static NAT44 in the kernel (dnat44_static, snat44_static). Off by default:
+// with mask 0 a GR_HIP_NH_T_DNAT nexthop's packets leave at
+// GR_HIP_E_DNAT44_STATIC and those towards a GR_HIP_IFACE_F_SNAT_STATIC iface
+// at GR_HIP_E_IP_OUTPUT_SNAT, for the CPU nodes.
+//   GR_HIP_NAT44_DNAT_STATIC: a packet whose nexthop is a DNAT one (and whose
+//     ip_input nh-type edge is still GR_HIP_E_DNAT44_STATIC) gets its
+//     destination and checksums rewritten (modules/policy/datapath/
+//     dnat44_static.c:37-89), a second FIB lookup in the ingress VRF, and goes
+//     on from there: GR_HIP_E_IP_ERROR_DEST_UNREACH, GR_HIP_E_IP_INPUT_LOCAL or
+//     ip_forward with the new nexthop (verdict.nh).
+//   GR_HIP_NAT44_SNAT_STATIC: a packet leaving through an iface with
+//     SNAT_STATIC and without SNAT_DYNAMIC is looked up in the rules below by
+//     (iface, source); a hit rewrites the source and checksums
+//     (modules/policy/datapath/snat44_static.c:10-54), a miss changes nothing,
+//     and both go on to eth_output. An iface with SNAT_DYNAMIC keeps
+//     GR_HIP_E_IP_OUTPUT_SNAT (conntrack lives on the CPU).
+// The kernel sees 64 bytes of each frame: a first fragment whose TCP / UDP
+// checksum field lies past them (IHL > 8 / > 10) is left untouched and takes
+// the CPU edge as with mask 0. Batches with GR_HIP_BATCH_F_PREFIX32 run with
+// mask 0 (the rewritten bytes lie past their 32). The mask holds for submits
+// issued after the call; it rebuilds no table.
+#define GR_HIP_NAT44_DNAT_STATIC 0x1
+#define GR_HIP_NAT44_SNAT_STATIC 0x2
+int gr_hip_nat44_set(gr_hip_ctx_t *, uint32_t mask);
+int gr_hip_nat44_get(gr_hip_ctx_t *); // the mask, or -EINVAL
+// The static SNAT rules, keyed {iface_id, match} as snat44_static_policy_add
+// (modules/policy/control/snat44_static.c:15-30); addresses in network byte
+// order. add: -EEXIST for a key already there; del: -ENOENT for a missing one;
+// clear removes every rule. Visible to submits issued after the call.
+int gr_hip_snat44_static_add(gr_hip_ctx_t *, uint16_t iface_id, uint32_t match_be, uint32_t replace_be);
+int gr_hip_snat44_static_del(gr_hip_ctx_t *, uint16_t iface_id, uint32_t match_be);
+int gr_hip_snat44_static_clear(gr_hip_ctx_t *);
 
 // RIB + device FIB (DIR24_8-equivalent; 2-byte entries while slots fit 15
 // bits). Routes are staged in the host RIB (adds and deletes never touch the
