@@ -35,6 +35,7 @@ EDGE_CHAIN6 = 0xFE  # eth_input type edge: continue into ip6_input on the GPU
 LINE = 64
 BATCH_F_LINES_ONLY = 0x1
 META_WALK = 0x4000  # gr_hip_pkt_meta.vlan_ck: this packet starts a graph walk
+META_RSS_HASH = 0x8000  # gr_hip_pkt_meta.vlan_ck: the mbuf had RTE_MBUF_F_RX_RSS_HASH (bond_output, algo RSS)
 MBUF_F_WALK = 0x01  # gr_hip_mbuf.flags: this mbuf starts a graph walk
 
 # enum gr_hip_edge, in order; names are the grout node each value stands for
@@ -108,6 +109,13 @@ NODE_DEPTH = 4  # GR_HIP_NODE_DEPTH: node walks in flight per queue
 # static NAT44 in the kernel (gr_hip_nat44_set) and its flags in gr_hip_verdict.domain
 NAT44_DNAT_STATIC, NAT44_SNAT_STATIC = 0x1, 0x2
 VERDICT_DNAT, VERDICT_SNAT, VERDICT_DOMAIN_MASK = 0x80, 0x40, 0x3F
+# bond_output in the kernel (gr_hip_bond_set, gr_hip_bond_output_set)
+BOND_MODE = {"ACTIVE_BACKUP": 1, "LACP": 2}
+BOND_ALGO = {"RSS": 1, "L2": 2, "L3_L4": 3}
+BOND_MAX_MEMBERS, BOND_RETA = 8, 256
+BOND_DT = np.dtype([("mode", "u1"), ("algo", "u1"), ("n_members", "u1"), ("active_member", "u1"),
+                    ("members", "<u2", (BOND_MAX_MEMBERS,)), ("_pad", "u1", (4,)), ("reta", "u1", (BOND_RETA,))])
+assert BOND_DT.itemsize == 280
 
 
 class Batch(ctypes.Structure):
@@ -159,6 +167,10 @@ HIP_API = {
     "gr_hip_snat44_static_add": (_I, [_P, _U16, _U32, _U32]),
     "gr_hip_snat44_static_del": (_I, [_P, _U16, _U32]),
     "gr_hip_snat44_static_clear": (_I, [_P]),
+    "gr_hip_bond_set": (_I, [_P, _U16, _P]),
+    "gr_hip_bond_del": (_I, [_P, _U16]),
+    "gr_hip_bond_output_set": (_I, [_P, _I]),
+    "gr_hip_bond_output_get": (_I, [_P]),
     "gr_hip_fib4_create": (_I, [_P, _U16, _U32, _U32]),
     "gr_hip_fib4_destroy": (_I, [_P, _U16]),
     "gr_hip_route4_add": (_I, [_P, _P, _U32, _I]),

@@ -311,13 +311,181 @@ __device__ __forceinline__ bool nat44_rewrite(uint8_t *R, uint32_t row, uint32_t
 	return true;
 }
 
+// ---- bond_output (modules/infra/datapath/bond_output.c:35-237)
+
+// rss_key (bond_output.c:37-41) as rte_softrss_be reads it (rte_thash.h):
+// ten little-endian words of the raw bytes (grout does not convert the key),
+// and a zero after them for the window of the last word.
+struct bond_key_t {
+	uint32_t k[11];
+};
+__host__ __device__ constexpr bond_key_t bond_key() {
+	return {{0xda565a6du, 0xc20e5b25u, 0x3d256741u, 0xb08fa343u, 0xcb2bcad0u, 0xb4307baeu, 0xa32dcb77u, 0x0cf23080u,
+		 0x3bb7426au, 0xfa01acbeu, 0}};
+}
+// What bit i (0 = LSB) of tuple word j contributes to the hash: the key's 32
+// bits from bit 32 * j + 31 - i on. i == 31: the second term is a shift by 32,
+// taken in 64 bits.
+__host__ __device__ constexpr uint32_t bond_win(int j, int i) {
+	const bond_key_t K = bond_key();
+	return (K.k[j] << (31 - i)) | (uint32_t)((uint64_t)K.k[j + 1] >> (i + 1));
+}
+
+#define BOND_TUPLE_MAX 36 // bytes: struct rte_ipv6_tuple
+
+// One byte of row `row` at byte offset off.
+__device__ __forceinline__ uint32_t lds_get8(const uint8_t *R, uint32_t row, uint32_t off) {
+	return R[row_off(row, off >> 4) + (off & 15)];
+}
+
+// Two bytes of row `row` at even byte offset off, as stored.
+__device__ __forceinline__ uint32_t lds_get16(const uint8_t *R, uint32_t row, uint32_t off) {
+	return *reinterpret_cast<const uint16_t *>(R + row_off(row, off >> 4) + (off & 15));
+}
+
+// rte_softrss_be is linear over GF(2): the hash of a tuple is the XOR of what
+// each of its bytes contributes at its position. bond_hash_byte(p, b): the
+// contribution of value b at tuple byte p. The loops over a tuple's bytes stay
+// rolled: the step is a cold branch of the chain and must not cost the plain
+// forward registers.
+#ifndef FWD4_BOND_BITWISE
+// From a table built at compile time, bond_tbl.t[p][b] (36 KiB, read-only):
+// one 4-byte load per tuple byte. The form measured against it is the bit
+// loop below (-DFWD4_BOND_BITWISE).
+struct bond_tbl_t {
+	uint32_t t[BOND_TUPLE_MAX][256];
+};
+constexpr bond_tbl_t make_bond_tbl() {
+	bond_tbl_t T{};
+	for (int p = 0; p < BOND_TUPLE_MAX; p++)
+		for (int b = 1; b < 256; b++) {
+			int low = 0;
+			while (!((b >> low) & 1))
+				low++;
+			T.t[p][b] = T.t[p][b & (b - 1)] ^ bond_win(p >> 2, 8 * (p & 3) + low);
+		}
+	return T;
+}
+static __device__ const bond_tbl_t bond_tbl = make_bond_tbl();
+
+__device__ __forceinline__ uint32_t bond_hash_byte(uint32_t p, uint32_t b) {
+	return bond_tbl.t[p][b];
+}
+#else
+// Branch-free over the byte's eight bits: bit k of byte p is bit i = 8 * (p % 4)
+// + k of word j = p / 4, whose window is the low half of (K[j] : K[j + 1]) >> (i + 1).
+static __device__ const bond_key_t bond_key_d = bond_key();
+
+__device__ __forceinline__ uint32_t bond_hash_byte(uint32_t p, uint32_t b) {
+	const uint64_t kk = ((uint64_t)bond_key_d.k[p >> 2] << 32) | bond_key_d.k[(p >> 2) + 1];
+	const uint32_t i0 = 8 * (p & 3) + 1;
+	uint32_t h = 0;
+#pragma unroll
+	for (uint32_t k = 0; k < 8; k++)
+		h ^= (0u - ((b >> k) & 1)) & (uint32_t)(kk >> (i0 + k));
+	return h;
+}
+#endif
+
+// The hash of tuple bytes [p0, p0 + n) = bytes [off, off + n) of row `row`.
+__device__ __forceinline__ uint32_t bond_hash_line(const uint8_t *R, uint32_t row, uint32_t off, uint32_t n, uint32_t p0) {
+	uint32_t h = 0;
+#pragma nounroll
+	for (uint32_t k = 0; k < n; k++)
+		h ^= bond_hash_byte(p0 + k, lds_get8(R, row, off + k));
+	return h;
+}
+
+// The hash of the tuple word w (little-endian) at tuple byte p0.
+__device__ __forceinline__ uint32_t bond_hash_word(uint32_t w, uint32_t p0) {
+	uint32_t h = 0;
+#pragma nounroll
+	for (uint32_t k = 0; k < 4; k++)
+		h ^= bond_hash_byte(p0 + k, (w >> (8 * k)) & 0xff);
+	return h;
+}
+
+// bond_select_tx_member / hash_tx_member (bond_output.c:35-199) for the packet
+// in row `row`, as eth_output left it, leaving through the bond whose entry the
+// adjacency names (`bond`, fwd4_adj.bond). Returns the member's iface id, 0
+// for none -- or for an IPv4 packet whose ports lie past the line: either way
+// the packet keeps the bond edge. V6: the frame's ether type is IPv6 (after
+// eth_output it is one of the two, so the tuple is never the L2 one by default,
+// and the VLAN TCI, which port_tx inserts later, is 0).
+template <bool V6>
+__device__ __forceinline__ uint32_t bond_member(const kctx &P, const uint8_t *R, uint32_t row, const gr_hip_pkt_meta &m,
+						uint32_t bond) {
+	if (bond == 0 || bond > tload(&P.T->n_bonds))
+		return 0;
+	const fwd4_bond *B = tload(&P.T->bonds) + (bond - 1);
+	const uint4 b0 = gld4(B), b1 = gld4(reinterpret_cast<const uint4 *>(B) + 1);
+	const uint32_t mode = b0.x & 0xff, algo = (b0.x >> 8) & 0xff, n_members = (b0.x >> 16) & 0xff;
+	uint32_t idx;
+	if (mode == GR_HIP_BOND_MODE_ACTIVE_BACKUP) {
+		idx = b0.x >> 24;
+	} else if (mode == GR_HIP_BOND_MODE_LACP) {
+		if (n_members == 0)
+			return 0;
+		uint32_t hash;
+		if (algo == GR_HIP_BOND_ALGO_RSS && (m.vlan_ck & GR_HIP_META_RSS_HASH)) {
+			hash = m.rss; // m->hash.rss: only hash % 256 is used
+		} else if (algo == GR_HIP_BOND_ALGO_L2) { // :69-79: the destination MAC, then TCI 0
+			hash = bond_hash_line(R, row, 0, 6, 0);
+		} else if (algo == GR_HIP_BOND_ALGO_RSS || algo == GR_HIP_BOND_ALGO_L3_L4) {
+			uint32_t ports = 0; // sport | dport << 16, as stored
+			if (V6) { // :142-167: src 22-37, dst 38-53; sport 54-55, dport 56-57 of TCP / UDP
+				const uint32_t proto = lds_get8(R, row, 20);
+				if (proto == 6 || proto == 17)
+					ports = lds_get16(R, row, 54) | (lds_get16(R, row, 56) << 16);
+				hash = bond_hash_line(R, row, 22, 32, 0);
+			} else { // :100-141: src 26-29, dst 30-33; ports of an unfragmented TCP / UDP packet
+				const uint32_t proto = lds_get8(R, row, 23);
+				// fragment_offset == 0 compares the whole field, DF and MF included
+				if ((proto == 6 || proto == 17) && lds_get16(R, row, 20) == 0) {
+					const uint32_t l4 = 14 + 4 * (lds_get8(R, row, 14) & 0xf);
+					if (l4 + 4 > GR_HIP_LINE)
+						return 0; // the ports are not in the line: the CPU node's packet
+					ports = lds_get16(R, row, l4) | (lds_get16(R, row, l4 + 2) << 16);
+				}
+				hash = bond_hash_line(R, row, 26, 8, 0);
+			}
+			// the tuple has dport first, then sport
+			hash ^= bond_hash_word((ports >> 16) | (ports << 16), V6 ? 32 : 8);
+		} else {
+			return 0;
+		}
+		idx = gld(&B->reta[hash & (GR_HIP_BOND_RETA - 1)]);
+	} else {
+		return 0;
+	}
+	if (idx >= n_members || idx >= GR_HIP_BOND_MAX_MEMBERS)
+		return 0;
+	const uint32_t w = idx < 2 ? b0.y : idx < 4 ? b0.z : idx < 6 ? b0.w : b1.x;
+	return (idx & 1) ? w >> 16 : w & 0xffff;
+}
+
+// bond_output_process (bond_output.c:201-237) for a packet iface_output sent
+// to bond_output: with a member, port_output with the member as the iface and
+// the member's tx counters (IFACE_STATS_INC :227) beside iface_output's.
+template <bool V6>
+__device__ __forceinline__ void bond_output(const kctx &P, const uint8_t *R, uint32_t row, const gr_hip_pkt_meta &m,
+					    uint32_t bond, result &r) {
+	const uint32_t member = bond_member<V6>(P, R, row, m, bond);
+	if (member == 0)
+		return; // bond_no_member, or not decidable here: the bond edge as before
+	r.edge = GR_HIP_E_PORT_OUTPUT;
+	r.iface = member;
+	r.tx_mem = member;
+}
+
 // From the adjacency (its first 32 bytes in a, b) to the verdict:
 // group resolution, ip_input's nexthop checks, dnat44_static (A.nat),
 // ip_forward, ip_output with snat44_static (A.nat), eth_output,
-// iface_output. Rewrites row `row` of R. nat: fwd4_params.nat.
+// iface_output, bond_output (A.bond). Rewrites row `row` of R. nat, bond:
+// fwd4_params.nat, .bond.
 __device__ __forceinline__ void chain_tail(const kctx &P, uint8_t *R, uint32_t row, const gr_hip_pkt_meta &m,
-					  uint32_t rx_flags, uint32_t nat, result &r, uint32_t dst, uint32_t data_len,
-					  uint32_t slot, uint4 a, uint4 b) {
+					  uint32_t rx_flags, uint32_t nat, uint32_t bond, result &r, uint32_t dst,
+					  uint32_t data_len, uint32_t slot, uint4 a, uint4 b) {
 	adjv A = unpack_adj(a, b, uint4{0, 0, 0, 0});
 	if (A.type == GR_HIP_NH_T_GROUP) {
 		slot = group_member(P, m, slot);
@@ -427,6 +595,8 @@ __device__ __forceinline__ void chain_tail(const kctx &P, uint8_t *R, uint32_t r
 		r.tx_par = A.tx_par;
 	}
 	lds_put(R, row, 0, c0);
+	if (bond && A.e_post == GR_HIP_E_BOND_OUTPUT)
+		bond_output<false>(P, R, row, m, gld(&tload(&P.T->adj)[r.nh].bond), r);
 }
 
 
@@ -576,7 +746,7 @@ __device__ __forceinline__ uint32_t fib6_rest(const fwd4_rx6 &v, const uint32_t 
 // row `row` of R, eth_input done (domain in r, data_len = the mbuf's after
 // its adj). Rewrites the hop limit and the L2 header in R.
 __device__ __forceinline__ void chain6(const kctx &P, uint8_t *R, uint32_t row, const gr_hip_pkt_meta &m,
-				       const rxv &rx, result &r, uint32_t data_len) {
+				       const rxv &rx, uint32_t bond, result &r, uint32_t data_len) {
 	if (data_len < 40) { // ip6_input.c:63-70
 		r.edge = GR_HIP_E_IP6_INPUT_BAD_LENGTH;
 		return;
@@ -754,6 +924,8 @@ __device__ __forceinline__ void chain6(const kctx &P, uint8_t *R, uint32_t row, 
 		r.tx_par = a.w >> 16;
 	}
 	lds_put(R, row, 0, c0);
+	if (bond && e_post == GR_HIP_E_BOND_OUTPUT)
+		bond_output<true>(P, R, row, m, c.w, r); // fwd4_adj6.bond
 }
 
 // ---- eth_output's per-walk source-MAC cache (eth_output.c:37-59)

@@ -269,6 +269,7 @@ __device__ __forceinline__ uint32_t bswap16(uint32_t x) {
 struct result {
 	uint32_t edge, domain, iface, nh;
 	uint32_t rx_if, rx_par, tx_if, tx_par; // counter keys (0 = none)
+	uint32_t tx_mem; // and the bond member bond_output sent the packet to
 };
 
 

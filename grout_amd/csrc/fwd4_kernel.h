@@ -7,6 +7,7 @@
 
 #include "../../include/grout_hip.h"
 
+#include <stddef.h>
 #include <stdint.h>
 
 #define FWD4_STAT_SLOTS 32 // per-block iface counter slots (LDS)
@@ -84,7 +85,8 @@ struct fwd4_adj {
 	uint16_t reta_size;
 	uint32_t reta_off;
 	uint32_t single;
-	uint32_t _pad[5];
+	uint32_t bond; // e_post BOND_OUTPUT: 1 + index of post_iface's fwd4_bond (0: none, the CPU node's)
+	uint32_t _pad[4];
 };
 
 // Per-nexthop IPv6 adjacency, 64 bytes: fwd4_adj for the ip6_input /
@@ -105,8 +107,13 @@ struct fwd4_adj6 {
 	uint8_t dmac[6];
 	uint8_t smac[6];
 	uint8_t ipv6[16];
-	uint32_t _pad[5];
+	uint32_t bond; // as fwd4_adj.bond (the same offset, 44)
+	uint32_t _pad[4];
 };
+
+static_assert(sizeof(struct fwd4_adj) == 64 && sizeof(struct fwd4_adj6) == 64
+		      && offsetof(struct fwd4_adj, bond) == 44 && offsetof(struct fwd4_adj6, bond) == 44,
+	      "adjacencies: 64 bytes, bond in the third 16-byte word of both");
 
 // Fast adjacency, 16 bytes: a nexthop whose packets take the plain forward
 // (L3, no LOCAL/LINK flag, ip_output/eth_output/iface_output all chain to
@@ -119,6 +126,20 @@ struct fwd4_nhf {
 	uint8_t smac[6];
 	uint16_t mtu;
 };
+
+// What bond_output reads of a bond iface (gr_hip_bond), 288 bytes: the head
+// in one 32-byte read, then one byte of the redirection table.
+struct fwd4_bond {
+	uint8_t mode; // GR_HIP_BOND_MODE_*
+	uint8_t algo; // GR_HIP_BOND_ALGO_*
+	uint8_t n_members;
+	uint8_t active_member;
+	uint16_t members[GR_HIP_BOND_MAX_MEMBERS];
+	uint8_t _pad[12];
+	uint8_t reta[GR_HIP_BOND_RETA];
+};
+
+static_assert(sizeof(struct fwd4_bond) == 288 && offsetof(struct fwd4_bond, reta) == 32, "fwd4_bond layout");
 
 // Home slot (before the mask) of a static SNAT rule's key, host and device.
 static inline
@@ -151,6 +172,8 @@ struct fwd4_tables {
 	// (iface_id + 1) << 32 | match (network order as stored), 0 = empty
 	const uint64_t *snat_keys;
 	const uint32_t *snat_vals; // replace, network order as stored
+	const struct fwd4_bond *bonds; // [n_bonds], named by fwd4_adj.bond - 1
+	uint32_t n_bonds;
 	uint32_t reta_cap;
 	uint32_t vlan_mask; // capacity - 1
 	uint32_t snat_mask; // capacity - 1
@@ -191,6 +214,8 @@ struct fwd4_params {
 	uint32_t wg0, wgs;
 	uint32_t ptrs;
 	uint32_t nat; // GR_HIP_NAT44_* the chain runs itself for this batch (0 with GR_HIP_BATCH_F_PREFIX32)
+	uint32_t bond; // 1: the chain runs bond_output itself for this batch (gr_hip_bond_output_set)
+	uint32_t _pad;
 };
 
 // The resident kernel's batches: ring r of a context holds `ndesc`

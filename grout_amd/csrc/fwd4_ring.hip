@@ -367,7 +367,7 @@ __device__ void ring_compute(const fwd4_params &A, const kctx &P, LT &L, stat_sl
 		else
 			rx = load_rx(P, m.iface);
 
-		result r = {GR_HIP_E_PUNT, 0, m.iface, 0, 0, 0, 0, 0};
+		result r = {GR_HIP_E_PUNT, 0, m.iface, 0, 0, 0, 0, 0, 0};
 		uint32_t fam = 0; // the packet entered ip_input (1) / ip6_input (2)
 		// from the FIB's nexthop slot to the verdict
 		auto tail4 = [&](uint32_t slot, uint32_t dst, uint32_t data_len) {
@@ -380,7 +380,7 @@ __device__ void ring_compute(const fwd4_params &A, const kctx &P, LT &L, stat_sl
 					fast_tail(R, lane, r, data_len, slot, f);
 				} else {
 					const uint4 *ap = reinterpret_cast<const uint4 *>(tload(&P.T->adj) + slot);
-					chain_tail(P, R, lane, m, rx.flags, A.nat, r, dst, data_len, slot, gld4(ap), gld4(ap + 1));
+					chain_tail(P, R, lane, m, rx.flags, A.nat, A.bond, r, dst, data_len, slot, gld4(ap), gld4(ap + 1));
 				}
 			}
 		};
@@ -390,7 +390,7 @@ __device__ void ring_compute(const fwd4_params &A, const kctx &P, LT &L, stat_sl
 		// costs IPv4)
 		auto tail6 = [&](uint32_t data_len) {
 			__builtin_amdgcn_s_setprio(2);
-			chain6(P, R, lane, m, rx, r, data_len);
+			chain6(P, R, lane, m, rx, A.bond, r, data_len);
 			__builtin_amdgcn_s_setprio(0);
 		};
 		if constexpr (SG == 0) {
@@ -444,6 +444,8 @@ __device__ void ring_compute(const fwd4_params &A, const kctx &P, LT &L, stat_sl
 			wave_count(slots, P, r.rx_par ? r.rx_par + 1 : 0, len);
 			wave_count(slots, P, r.tx_if ? (r.tx_if | 0x10000u) + 1 : 0, len);
 			wave_count(slots, P, r.tx_par ? (r.tx_par | 0x10000u) + 1 : 0, len);
+			if (A.bond)
+				wave_count(slots, P, r.tx_mem ? (r.tx_mem | 0x10000u) + 1 : 0, len);
 		}
 	}
 }

@@ -372,6 +372,13 @@ struct gr_hip_ctx {
 	uint64_t *d_snat_keys = nullptr;
 	uint32_t *d_snat_vals = nullptr;
 	uint32_t snat_cap = 0;
+	// bond_output in the kernel (gr_hip_bond_set, gr_hip_bond_output_set): the
+	// bonds by iface id, their device table in that order (fwd4_tables.bonds; an
+	// adjacency names its bond's rank + 1), and the switch
+	std::map<uint16_t, gr_hip_bond> bonds;
+	fwd4_bond *d_bonds = nullptr;
+	uint32_t bonds_cap = 0;
+	std::atomic<int> bond_on{0};
 	fwd4_edges edges;
 	fwd4_tables *d_tables[2]; // device copy of what every launch reads, by generation
 	std::vector<gr_hip_queue *> queues;
@@ -588,6 +595,12 @@ static void fill_post(const gr_hip_ctx *c, const gr_hip_nh &nh, const gr_hip_ifa
 	a.tx_par = out != oif ? out->id : 0;
 	a.post_iface = out->id;
 	a.e_post = out->type < 8 ? E.iout_type[out->type] : GR_HIP_E_IFACE_OUTPUT_INVAL_TYPE;
+	// bond_output's view of the bond, for launches that run it (fwd4_params.bond)
+	if (a.e_post == GR_HIP_E_BOND_OUTPUT && out->type == GR_HIP_IFACE_TYPE_BOND) {
+		const auto it = c->bonds.find(out->id);
+		if (it != c->bonds.end())
+			a.bond = 1 + (uint32_t)std::distance(c->bonds.begin(), it);
+	}
 }
 
 // IPv6 adjacency of nexthop `slot`: ip6_input's view (ip6_input.c:133-144)
@@ -788,6 +801,8 @@ static int upload_tables(gr_hip_ctx *c) {
 		t[g].snat_keys = c->d_snat_keys;
 		t[g].snat_vals = c->d_snat_vals;
 		t[g].snat_mask = c->snat_cap ? c->snat_cap - 1 : 0;
+		t[g].bonds = c->d_bonds;
+		t[g].n_bonds = c->d_bonds ? (uint32_t)c->bonds.size() : 0;
 		t[g].max_ifaces = c->max_ifaces;
 		t[g].max_nh = c->max_nh;
 		t[g].edges = c->edges;
@@ -1010,6 +1025,7 @@ extern "C" int gr_hip_fini(gr_hip_ctx_t *c) {
 	hipFree(c->d_vlan_vals);
 	hipFree(c->d_snat_keys);
 	hipFree(c->d_snat_vals);
+	hipFree(c->d_bonds);
 	for (int i = 0; i < 2; i++) {
 		hipHostFree(c->stage[i]);
 		if (c->stage_ev[i])
@@ -1293,6 +1309,101 @@ extern "C" int gr_hip_snat44_static_clear(gr_hip_ctx_t *c) {
 	return snat_change(c);
 }
 
+// Rebuild the device table of the bonds (fwd4_tables.bonds, in c->bonds'
+// order) and the adjacencies, which name a bond by its rank. Caller holds
+// c->mu exclusively and has quiesced.
+static int upload_bonds(gr_hip_ctx *c) {
+	const uint32_t n = (uint32_t)c->bonds.size();
+	std::vector<fwd4_bond> img(n);
+	uint32_t i = 0;
+	for (const auto &kv : c->bonds) {
+		fwd4_bond &d = img[i++];
+		const gr_hip_bond &b = kv.second;
+		memset(&d, 0, sizeof(d));
+		d.mode = b.mode;
+		d.algo = b.algo;
+		d.n_members = b.n_members;
+		d.active_member = b.active_member;
+		memcpy(d.members, b.members, sizeof(d.members));
+		memcpy(d.reta, b.reta, sizeof(d.reta));
+	}
+	if (n > c->bonds_cap) {
+		uint32_t cap = c->bonds_cap ? c->bonds_cap : 16; // grown, never shrunk
+		while (cap < n)
+			cap *= 2;
+		hipFree(c->d_bonds);
+		c->d_bonds = nullptr;
+		c->bonds_cap = 0;
+		HCK(hipMalloc(&c->d_bonds, cap * sizeof(fwd4_bond)));
+		c->bonds_cap = cap;
+	}
+	int r = n ? h2d(c, c->d_bonds, img.data(), n * sizeof(fwd4_bond)) : 0;
+	if (r == 0)
+		r = ctl_sync(c); // img goes out of scope
+	if (r == 0)
+		r = upload_tables(c);
+	if (r == 0)
+		r = upload_views(c, false, 0, 0, true);
+	return r;
+}
+
+extern "C" int gr_hip_bond_set(gr_hip_ctx_t *c, uint16_t iface_id, const struct gr_hip_bond *b) {
+	if (c == nullptr || b == nullptr || iface_id == 0 || iface_id >= c->max_ifaces
+	    || b->n_members > GR_HIP_BOND_MAX_MEMBERS)
+		return -EINVAL;
+	std::lock_guard<std::shared_mutex> l(c->mu);
+	const gr_hip_iface *bi = iface_get(c, iface_id);
+	if (bi == nullptr || bi->type != GR_HIP_IFACE_TYPE_BOND)
+		return -EINVAL;
+	for (uint32_t i = 0; i < b->n_members; i++) { // bond members are ports (bond.c bond_attach_member)
+		const gr_hip_iface *m = iface_get(c, b->members[i]);
+		if (m == nullptr || m->type != GR_HIP_IFACE_TYPE_PORT)
+			return -EINVAL;
+	}
+	hipSetDevice(c->dev);
+	const auto old = c->bonds.find(iface_id);
+	const bool had = old != c->bonds.end();
+	const gr_hip_bond prev = had ? old->second : gr_hip_bond{};
+	c->bonds[iface_id] = *b;
+	int r = quiesce(c);
+	if (r == 0)
+		r = upload_bonds(c);
+	if (r) { // not on the device: not set
+		if (had)
+			c->bonds[iface_id] = prev;
+		else
+			c->bonds.erase(iface_id);
+	}
+	return r;
+}
+
+extern "C" int gr_hip_bond_del(gr_hip_ctx_t *c, uint16_t iface_id) {
+	if (c == nullptr)
+		return -EINVAL;
+	std::lock_guard<std::shared_mutex> l(c->mu);
+	if (c->bonds.erase(iface_id) == 0)
+		return -ENOENT;
+	hipSetDevice(c->dev);
+	int r = quiesce(c);
+	if (r == 0)
+		r = upload_bonds(c);
+	return r;
+}
+
+extern "C" int gr_hip_bond_output_set(gr_hip_ctx_t *c, int on) {
+	if (c == nullptr)
+		return -EINVAL;
+	// like the NAT mask: a submit runs entirely with the old value or the new
+	// one; the adjacencies name their bonds either way, so nothing is rebuilt
+	std::lock_guard<std::shared_mutex> l(c->mu);
+	c->bond_on.store(on != 0, std::memory_order_relaxed);
+	return 0;
+}
+
+extern "C" int gr_hip_bond_output_get(gr_hip_ctx_t *c) {
+	return c == nullptr ? -EINVAL : c->bond_on.load(std::memory_order_relaxed);
+}
+
 extern "C" int gr_hip_iface_set(gr_hip_ctx_t *c, const struct gr_hip_iface *ifs, uint32_t n) {
 	if (c == nullptr || (ifs == nullptr && n))
 		return -EINVAL;
@@ -1322,7 +1433,10 @@ extern "C" int gr_hip_iface_del(gr_hip_ctx_t *c, uint16_t id) {
 	hipSetDevice(c->dev);
 	bool vlan = c->ifaces[id].type == GR_HIP_IFACE_TYPE_VLAN;
 	c->ifaces[id] = gr_hip_iface {};
+	const bool bond = c->bonds.erase(id) != 0;
 	int r = quiesce(c);
+	if (r == 0 && bond) // the bonds after it change rank
+		r = upload_bonds(c);
 	if (r == 0)
 		r = upload_views(c, true, 0, 0, true);
 	if (r == 0 && vlan)
@@ -2285,6 +2399,7 @@ static int launch(gr_hip_queue *q, hipStream_t s, const gr_hip_batch *b, bool ti
 		: (b->flags & GR_HIP_BATCH_F_FRAME_PTRS)    ? UINT32_MAX // whole frames
 							    : b->in_stride;
 	A.nat = batch_nat(c, b);
+	A.bond = (uint32_t)c->bond_on.load(std::memory_order_relaxed);
 	A.nhf_lds = 0;
 	int stats = c->stats_on && q->d_stats != nullptr;
 	uint32_t slot = (uint32_t)(q->n_launch % N_TIMED);
@@ -2743,6 +2858,7 @@ static int res_post(gr_hip_queue *q, const gr_hip_batch *b, res_mark *m) {
 		: (b->flags & GR_HIP_BATCH_F_FRAME_PTRS)    ? UINT32_MAX
 							    : b->in_stride;
 	A.nat = batch_nat(c, b);
+	A.bond = (uint32_t)c->bond_on.load(std::memory_order_relaxed);
 	A.spin_max = c->spin_max;
 	A.err = q->d_err;
 	A.wgs = k;

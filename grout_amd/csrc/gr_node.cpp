@@ -252,7 +252,8 @@ extern "C" uint64_t gr_node_stage_mbufs(void *const *mbufs, uint32_t n, const st
 		const uint8_t *mb = static_cast<const uint8_t *>(mbufs[i]);
 		const uint8_t *priv = mb + L.priv;
 		const uint8_t *ifp = get<const uint8_t *>(priv, L.priv_iface);
-		const uint64_t ck = get<uint64_t>(mb, L.ol_flags) & L.ck_mask;
+		const uint64_t ol_flags = get<uint64_t>(mb, L.ol_flags);
+		const uint64_t ck = ol_flags & L.ck_mask;
 		const uint32_t pkt_len = get<uint32_t>(mb, L.pkt_len);
 		const uint8_t st = ck == L.ck_good ? GR_HIP_CKSUM_GOOD : ck == L.ck_bad ? GR_HIP_CKSUM_BAD : GR_HIP_CKSUM_UNKNOWN;
 		pos[i] = (uint32_t)p;
@@ -261,7 +262,8 @@ extern "C" uint64_t gr_node_stage_mbufs(void *const *mbufs, uint32_t n, const st
 			memcpy(lb + (size_t)p * GR_HIP_LINE, gr_node_frame(mb, lay), GR_HIP_LINE);
 		meta[p].iface = ifp != nullptr ? get<uint16_t>(ifp, L.iface_id) : 0;
 		meta[p].vlan_ck = (uint16_t)((get<uint16_t>(priv, L.priv_vlan_id) & 0xfff) | (st << 12)
-					     | (start ? GR_HIP_META_WALK : 0));
+					     | (start ? GR_HIP_META_WALK : 0)
+					     | ((ol_flags & 2) ? GR_HIP_META_RSS_HASH : 0)); // RTE_MBUF_F_RX_RSS_HASH
 		meta[p].pkt_len = (uint16_t)(pkt_len > 0xffff ? 0xffff : pkt_len);
 		meta[p].rss = (uint16_t)get<uint32_t>(mb, L.rss);
 		p++;
@@ -352,6 +354,19 @@ static inline void count(struct gr_hip_iface_stats *st, uint32_t n_st, uint32_t 
 		st[id].rx_packets++;
 		st[id].rx_bytes += len;
 	}
+}
+
+// The third iface iface_output and bond_output count for a packet whose
+// nexthop leaves through the VLAN sub-interface `oif` of a bond and that the
+// kernel's bond_output sent to the member port `post`: the bond itself
+// (iface_output counted it as the sub-interface's parent, iface_output.c:103-105,
+// before bond_output.c:227 counted the member). 0 (counted nowhere) otherwise:
+// a VLAN's parent is the verdict's iface whenever the kernel selected no member.
+static inline uint32_t bond_above(const struct gr_hip_iface *ifaces, uint32_t n_ifaces, uint32_t oif, uint32_t post) {
+	if (ifaces == nullptr || oif >= n_ifaces || ifaces[oif].id != oif || ifaces[oif].type != GR_HIP_IFACE_TYPE_VLAN)
+		return 0;
+	const uint32_t par = ifaces[oif].parent_id;
+	return par != post && par < n_ifaces && ifaces[par].id == par && ifaces[par].type == GR_HIP_IFACE_TYPE_BOND ? par : 0;
 }
 
 // The hand-back's prefetch distance and locality (measurement builds
@@ -463,8 +478,10 @@ static inline bool port_output_fast(struct gr_node_direct *d, uint32_t i, const 
 	if (ifst != nullptr) {
 		count(ifst, n_ifst, b.iface, false, b.pkt_len);
 		count(ifst, n_ifst, oif, true, b.pkt_len);
-		if (v.iface != oif)
+		if (v.iface != oif) {
 			count(ifst, n_ifst, v.iface, true, b.pkt_len);
+			count(ifst, n_ifst, bond_above(ifaces, n_ifaces, oif, v.iface), true, b.pkt_len);
+		}
 	}
 	if (ifp == nullptr && v.iface != 0) {
 		d->stale++; // see to_mbuf
@@ -671,8 +688,10 @@ extern "C" int gr_node_apply_ex(
 				    && v.edge != GR_HIP_E_IFACE_OUTPUT_VLAN_NO_PARENT && v.nh && v.nh < n_nh && nh != nullptr) {
 					const uint16_t oif = nh[v.nh].iface_id;
 					count(ifst, n_ifst, oif, true, len0);
-					if (v.iface != oif)
+					if (v.iface != oif) {
 						count(ifst, n_ifst, v.iface, true, len0);
+						count(ifst, n_ifst, bond_above(ifaces, n_ifaces, oif, v.iface), true, len0);
+					}
 				}
 			}
 			b.iface = v.iface;

@@ -157,8 +157,24 @@ class FastPath:
     def snat44_static_clear(self):
         check("gr_hip_snat44_static_clear", self.lib.gr_hip_snat44_static_clear(self.h))
 
+    # -- bond_output -----------------------------------------------------------
+    def bond_set(self, iface_id, bond):
+        """What bond_output reads of bond iface_id (gr_hip_bond_set); bond: one abi.BOND_DT record."""
+        a = np.ascontiguousarray(bond, dtype=abi.BOND_DT).reshape(1)
+        check("gr_hip_bond_set", self.lib.gr_hip_bond_set(self.h, iface_id, ptr(a)))
+
+    def bond_del(self, iface_id):
+        check("gr_hip_bond_del", self.lib.gr_hip_bond_del(self.h, iface_id))
+
+    def bond_output_set(self, on=True):
+        """Whether the kernel runs bond_output itself (gr_hip_bond_output_set); off by default."""
+        check("gr_hip_bond_output_set", self.lib.gr_hip_bond_output_set(self.h, 1 if on else 0))
+
+    def bond_output_get(self):
+        return check("gr_hip_bond_output_get", self.lib.gr_hip_bond_output_get(self.h))
+
     def load(self, topo):
-        """Push a grout_amd.topology.Topology (ifaces, nexthops, reta, FIBs, static SNAT rules)."""
+        """Push a grout_amd.topology.Topology (ifaces, nexthops, reta, FIBs, static SNAT rules, bonds)."""
         # the rule list is the topology's (an older library under A/B,
         # GR_HIP_AB_OLD, has no rules to clear)
         if topo.snat44_static or hasattr(self.lib, "gr_hip_snat44_static_clear"):
@@ -166,6 +182,8 @@ class FastPath:
         for iface_id, match, replace in topo.snat44_static:
             self.snat44_static_add(iface_id, match, replace)
         self.set_ifaces(topo.ifaces)
+        for iface_id, bond in getattr(topo, "bonds", {}).items():  # their ifaces are set: members are checked
+            self.bond_set(iface_id, bond)
         if topo.n_nh:
             self.set_nexthops(topo.nh[1:topo.n_nh + 1], first=1)
         self.set_reta(topo.reta)

@@ -60,6 +60,7 @@ class Topology:
         self.routes6 = []  # list of ROUTE6_DT arrays
         self.fibs6 = {}  # vrf_id -> (max_routes, num_groups)
         self.snat44_static = []  # (iface_id, match, replace), host-order ints
+        self.bonds = {}  # bond iface id -> abi.BOND_DT record (add_bond)
 
     # -- interfaces ---------------------------------------------------------
     def _iface(self, iface_id, itype, mode, flags, mtu, vrf_id, mac, **kw):
@@ -153,6 +154,38 @@ class Topology:
                                 state=abi.NH_S["REACHABLE"])
         self.add_route(self.ifaces[iface_id]["vrf_id"], f"{net.ip}/{net.network.prefixlen}", slot)
         return slot
+
+    # -- bonds ------------------------------------------------------------------
+    def add_bond(self, iface_id, mode, algo, members, active=None, primary=None):
+        """What bond_output reads of bond iface_id (iface_info_bond): mode and
+        algo (names of abi.BOND_MODE / BOND_ALGO, or raw values), the member
+        port iface ids, and which of them are active (all by default; for
+        LACP those in COLLECTING_DISTRIBUTING). As bond_update_active_members
+        (modules/infra/control/bond.c:245-340) leaves it: LACP gets
+        reta[i] = active_ids[i % n_active], all 0xff with no active member;
+        active-backup gets active_member = the primary when it is active, else
+        the first active member, 0xff (none) when there is none."""
+        members = [int(m) for m in members]
+        if len(members) > abi.BOND_MAX_MEMBERS:
+            raise ValueError("bond members")
+        active = members if active is None else [int(m) for m in active]
+        ids = [i for i, m in enumerate(members) if m in active]
+        b = np.zeros((), dtype=abi.BOND_DT)
+        b["mode"] = abi.BOND_MODE.get(mode, mode)
+        b["algo"] = abi.BOND_ALGO.get(algo, algo)
+        b["n_members"] = len(members)
+        b["members"][:len(members)] = members
+        b["reta"] = 0xFF
+        b["active_member"] = 0xFF
+        if b["mode"] == abi.BOND_MODE["LACP"]:
+            if ids:
+                b["reta"] = [ids[i % len(ids)] for i in range(abi.BOND_RETA)]
+        elif ids:  # the table is filled with the one active id too (:322-325)
+            p = members.index(primary) if primary in members else None
+            b["active_member"] = p if p in ids else ids[0]
+            b["reta"] = b["active_member"]
+        self.bonds[iface_id] = b
+        return b
 
     # -- static NAT44 -----------------------------------------------------------
     def add_snat44_static(self, iface_id, match, replace):

@@ -281,7 +281,7 @@ struct gr_hip_pkt_meta {
 	uint16_t iface; // iface_mbuf_data.iface (RX port iface id)
 	uint16_t vlan_ck; // bits 0-11: iface_mbuf_data.vlan_id;
 	                  // bits 12-13: GR_HIP_CKSUM_* from ol_flags;
-	                  // bit 14: GR_HIP_META_WALK
+	                  // bit 14: GR_HIP_META_WALK; bit 15: GR_HIP_META_RSS_HASH
 	uint16_t pkt_len; // rte_pktmbuf_pkt_len == data_len (single segment)
 	uint16_t rss; // low 16 bits of m->hash.rss (reta_size <= 4096)
 };
@@ -295,6 +295,10 @@ struct gr_hip_pkt_meta {
 // this bit. The rte_graph node (gr_hip_node_process) sets it at the start
 // of each walk and pads so that no walk straddles a multiple of 64.
 #define GR_HIP_META_WALK 0x4000
+// The mbuf had RTE_MBUF_F_RX_RSS_HASH (ol_flags bit 1): `rss` is the NIC's hash.
+// Read only by the in-kernel bond_output (gr_hip_bond_output_set) of a bond
+// whose algo is GR_HIP_BOND_ALGO_RSS; nothing else looks at the bit.
+#define GR_HIP_META_RSS_HASH 0x8000
 
 // Output verdict, 8 bytes per packet.
 struct gr_hip_verdict {
@@ -436,6 +440,54 @@ int gr_hip_nat44_get(gr_hip_ctx_t *); // the mask, or -EINVAL
 int gr_hip_snat44_static_add(gr_hip_ctx_t *, uint16_t iface_id, uint32_t match_be, uint32_t replace_be);
 int gr_hip_snat44_static_del(gr_hip_ctx_t *, uint16_t iface_id, uint32_t match_be);
 int gr_hip_snat44_static_clear(gr_hip_ctx_t *);
+
+// bond_output in the kernel (modules/infra/datapath/bond_output.c:35-237).
+// Off by default: a packet whose iface_output result is a BOND iface leaves at
+// GR_HIP_E_BOND_OUTPUT with the bond as verdict.iface, for the CPU node. With
+// gr_hip_bond_output_set(ctx, 1) the kernel selects the member port itself and
+// such a packet leaves at GR_HIP_E_PORT_OUTPUT with the member as
+// verdict.iface, the member's tx counters incremented beside the bond's (and
+// the VLAN sub-interface's). Selection, by the bond's gr_hip_bond:
+//   mode ACTIVE_BACKUP: members[active_member] if active_member < n_members;
+//   mode LACP, n_members > 0: members[reta[hash % 256]] if that index is
+//     < n_members, where hash is, by algo,
+//       RSS: meta.rss when meta.vlan_ck has GR_HIP_META_RSS_HASH, else L3_L4;
+//       L2: the destination MAC eth_output wrote, and a zero VLAN TCI;
+//       L3_L4: source and destination address, then destination port and
+//         source port (struct rte_ipv4_tuple / rte_ipv6_tuple order) of TCP and
+//         UDP -- for IPv4 only when the whole fragment_offset field is 0, DF
+//         included, as grout compares it; ports 0 otherwise;
+//     hashed with rte_softrss_be over the 40 raw bytes of rss_key (bond_output.c:37-41).
+// A packet with no member (any other mode or algo, an empty bond, an index
+// past n_members), an IPv4 packet whose ports lie past the 64-byte line
+// (IHL > 11), and every packet of a bond without a gr_hip_bond keep
+// GR_HIP_E_BOND_OUTPUT and today's counters: grout's node drops or sends them.
+// The addresses hashed are those after the kernel's own NAT rewrites.
+#define GR_HIP_BOND_MODE_ACTIVE_BACKUP 1 // GR_BOND_MODE_ACTIVE_BACKUP
+#define GR_HIP_BOND_MODE_LACP 2 // GR_BOND_MODE_LACP
+#define GR_HIP_BOND_ALGO_RSS 1 // GR_BOND_ALGO_RSS
+#define GR_HIP_BOND_ALGO_L2 2 // GR_BOND_ALGO_L2
+#define GR_HIP_BOND_ALGO_L3_L4 3 // GR_BOND_ALGO_L3_L4
+#define GR_HIP_BOND_MAX_MEMBERS 8
+#define GR_HIP_BOND_RETA 256
+// Mirror of what bond_output reads of iface_info_bond (bond.h): 280 bytes.
+struct gr_hip_bond {
+	uint8_t mode; // GR_HIP_BOND_MODE_*
+	uint8_t algo; // GR_HIP_BOND_ALGO_*
+	uint8_t n_members;
+	uint8_t active_member; // ACTIVE_BACKUP: index into members
+	uint16_t members[GR_HIP_BOND_MAX_MEMBERS]; // PORT iface ids, [0, n_members)
+	uint8_t _pad[4];
+	uint8_t reta[GR_HIP_BOND_RETA]; // LACP: redirection_table, member indexes (0xff: none)
+};
+// set: -EINVAL for an iface that is not a BOND one, n_members > 8 or a member
+// that is not a PORT iface. del: -ENOENT when the iface has no entry. Deleting
+// the iface (gr_hip_iface_del) drops its entry. Visible to submits issued
+// after the call.
+int gr_hip_bond_set(gr_hip_ctx_t *, uint16_t iface_id, const struct gr_hip_bond *);
+int gr_hip_bond_del(gr_hip_ctx_t *, uint16_t iface_id);
+int gr_hip_bond_output_set(gr_hip_ctx_t *, int on);
+int gr_hip_bond_output_get(gr_hip_ctx_t *); // 0 / 1, or -EINVAL
 
 // RIB + device FIB (DIR24_8-equivalent; 2-byte entries while slots fit 15
 // bits). Routes are staged in the host RIB (adds and deletes never touch the
